@@ -2,7 +2,7 @@
 """Headline benchmark: output megapixels/s of the 8x EMSR stage-3 forward
 (5-slice 1x128x128 LR windows -> 1024x1024 HR tiles) on 1/2/4/8 MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: either launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the env), or started
 plainly -- then this process only PARSES the arguments and starts N fresh rank processes of itself (one per GPU,
@@ -81,7 +81,16 @@ def parse_args(argv=None):
     ap.add_argument("--gather", type=str, default="f32", choices=("f32", "u8"),
                     help="what the step's all-gather exchanges: the fp32 HR slabs (default; 4 MiB per 1024^2 tile, the north_star's slabs) or the "
                          "8-bit image the last kernel writes (1 MiB per tile: what output_GPEMSR.py saves)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="--mode forward: after the timed steps, write what the last timed step returned (out, ref_img) as DIR/<name>.npy in "
+                         "float32, at most 64 MB in all (a fixed, seeded sample of the elements of a larger array), so that two builds run "
+                         "with the same arguments can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.mode != "forward":
+        ap.error("--dump-outputs: only --mode forward")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -171,11 +180,22 @@ class _StubModel:
         return out, x
 
 
+def _barrier(dev):
+    """torch.distributed.barrier() asks the runtime which accelerator the machine has, and that initialises the GPU runtime even in a
+    CPU-only process: the CPU ranks of the launcher self-test (--stub) meet in a one-element all-reduce instead, so that on a GPU machine
+    they never open the device."""
+    import torch
+    if dev.type == "cpu":
+        torch.distributed.all_reduce(torch.zeros(1))
+    else:
+        torch.distributed.barrier()
+
+
 def timed_steps(step, steps: int, world: int, dev, sync):
     """EXACTLY `steps` steps between barrier + synchronize pairs; returns (max over ranks of the wall time, last output)."""
     import torch
     if world > 1:
-        torch.distributed.barrier()
+        _barrier(dev)
     sync()
     t0 = time.perf_counter()
     out = None
@@ -183,7 +203,7 @@ def timed_steps(step, steps: int, world: int, dev, sync):
         out = step()
     sync()
     if world > 1:
-        torch.distributed.barrier()
+        _barrier(dev)
     dt = time.perf_counter() - t0
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -195,12 +215,14 @@ def timed_steps(step, steps: int, world: int, dev, sync):
 PROFILED_STEPS = 3                  # steps of the second, event-carrying pass the kernel tables come from
 
 
-def measure_leg(step, args, world, dev, sync, stub=False):
+def measure_leg(step, args, world, dev, sync, stub=False, after_timed=None):
     """The OFFICIAL figure of a leg: exactly args.steps steps between barrier + synchronize pairs with NO per-launch events.  The kernel
     tables (roofline, per-kernel rows, layer report) come from a SECOND pass of min(steps, PROFILED_STEPS) steps with HIP events around every
-    matrix-kernel launch (ops.LaunchProfiler; events on the launch stream).  Returns (dt, last output, profiler or None, profiled-pass seconds,
-    profiled steps)."""
+    matrix-kernel launch (ops.LaunchProfiler; events on the launch stream).  after_timed(last output) runs between the two passes.  Returns
+    (dt, last output, profiler or None, profiled-pass seconds, profiled steps)."""
     dt, out = timed_steps(step, args.steps, world, dev, sync)
+    if after_timed is not None:
+        after_timed(out)
     if stub:
         return dt, out, None, dt, args.steps
     from gpemsr_amd import ops
@@ -212,6 +234,26 @@ def measure_leg(step, args, world, dev, sync, stub=False):
     finally:
         ops.PROFILER = None
     return dt, out, prof, dtp, psteps
+
+
+DUMP_BYTES = 64_000_000             # --dump-outputs: the .npy files together stay below this
+DUMP_SEED = 20260                   # seed of the element sample of an array too large for its share
+
+
+def dump_outputs(arrays: dict, dirname: str) -> None:
+    """--dump-outputs: every array as <dirname>/<name>.npy in float32.  An array larger than its equal share of DUMP_BYTES is written as a
+    1-D sample of its flattened elements: indices drawn without replacement by numpy's default_rng(DUMP_SEED), sorted.  The indices depend
+    on the array's size only, so two runs with the same arguments write the same elements."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    cap = (DUMP_BYTES // len(arrays) - 4096) // 4                     # float32 elements per array (4 KiB left for the .npy header)
+    for name, t in arrays.items():
+        a = t.detach()
+        if a.numel() > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.numel(), size=cap, replace=False, shuffle=False))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(dirname, name + ".npy"), a.to(torch.float32).cpu().numpy())
 
 
 def _family(summ, names):
@@ -695,10 +737,18 @@ def run_forward(args) -> int:
         model = build_model(opt, load_prior_files=False, precision=args.precision).eval().to(dev)
         x = synth_lr_tiles(B, 5, lr, lr, seed=1000 + rank, kind="uniform").to(dev)     # resident in HBM before timing
     timing = [] if world > 1 else None
+    last = {}
 
     def step():
-        out, _ = gdist.forward_sharded(model, x, rank, world, already_local=True, gather=True, gather_u8=args.gather == "u8", timing=timing)
+        out, ref = gdist.forward_sharded(model, x, rank, world, already_local=True, gather=True, gather_u8=args.gather == "u8", timing=timing)
+        if args.dump_outputs:
+            last["ref_img"] = ref
         return out
+
+    def dump(out):
+        if rank == 0:
+            dump_outputs({"out": out, "ref_img": last["ref_img"]}, args.dump_outputs)
+            print(f"[bench] last timed step's outputs written to {args.dump_outputs}", file=sys.stderr, flush=True)
 
     lap("setup")
     for _ in range(args.warmup):
@@ -706,7 +756,7 @@ def run_forward(args) -> int:
     if timing is not None:
         timing.clear()
     # the official number: K steps with NO per-launch events; the tables: a second, profiled pass (measure_leg)
-    dt, out, prof, dtp, psteps = measure_leg(step, args, world, dev, sync, stub=args.stub)
+    dt, out, prof, dtp, psteps = measure_leg(step, args, world, dev, sync, stub=args.stub, after_timed=dump if args.dump_outputs else None)
     rank_phases = gdist.step_phase_times(timing[:args.steps], world, dev) if timing is not None else None
     assert out.shape[0] == B * world
     rccl_world = torch.distributed.get_world_size() if world > 1 else 1           # the group the all-gathers above ran on

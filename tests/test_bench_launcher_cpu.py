@@ -152,3 +152,49 @@ def test_the_full_measurement_document_compacts_to_a_line_the_driver_keeps():
             assert line[k] > 0, k
         if d["n_gpus"] == 1:
             assert set(line["cpu_baseline"]) >= {"value", "unit", "cores", "kind", "sample"}
+
+
+def test_dump_outputs_writes_the_last_timed_steps_outputs(tmp_path):
+    """--dump-outputs DIR: what the timed path's caller receives from its last step, as float32 .npy files, the same on every run with the
+    same arguments (the stub's `out` is a function of its seeded input tile, `ref_img` the input itself)."""
+    import numpy as np
+    import torch
+    got = []
+    for run in ("a", "b"):
+        r = _run(["--gpus", "1", "--dump-outputs", str(tmp_path / run)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        got.append({n: np.load(tmp_path / run / f"{n}.npy") for n in ("out", "ref_img")})
+    assert sorted(os.listdir(tmp_path / "a")) == ["out.npy", "ref_img.npy"]
+    x = torch.rand(3, 5, 1, 16, 16, generator=torch.Generator().manual_seed(1000))
+    want = (x[:, 2].mean(dim=(1, 2, 3)).view(3, 1, 1, 1) + x[:, 2, :, :8, :8]).numpy()
+    for g in got:
+        assert g["out"].dtype == np.float32 and g["ref_img"].dtype == np.float32
+        assert np.array_equal(g["out"], want) and np.array_equal(g["ref_img"], x.numpy())
+    assert all(np.array_equal(got[0][n], got[1][n]) for n in ("out", "ref_img"))
+
+
+def test_dump_outputs_samples_large_arrays_under_64_mb(tmp_path):
+    """An output larger than its share of the 64 MB is written as a fixed, seeded sample of its elements: the same indices on every run,
+    the values exactly the array's at those indices."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(16_000_000, dtype=torch.float64).view(16, 1, 1000, 1000)     # < 2**24: exact in float32
+    small = torch.arange(6, dtype=torch.int32).view(2, 3)
+    for run in ("a", "b"):
+        bench.dump_outputs({"big": big, "small": small}, str(tmp_path / run))
+    sizes = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert sizes <= bench.DUMP_BYTES
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.ndim == 1 and 1_000_000 < a.size < big.numel()
+    assert np.array_equal(a, b)
+    assert (np.diff(a) > 0).all() and a[0] >= 0 and a[-1] < big.numel()       # distinct sorted indices of arange = the values themselves
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.numpy())
+
+
+def test_steps_and_warmup_are_checked():
+    for extra in (["--steps", "0"], ["--warmup", "-1"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--gpus", "1"] + extra, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "--steps must be >= 1" in r.stderr

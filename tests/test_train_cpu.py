@@ -113,10 +113,16 @@ def test_oracle_stage2_step_matches_reference_golden(golden_dir):
     assert abs(loss.item() - float(d["loss_1"])) <= 1e-5 * float(d["loss_1"])
     assert np.abs(logits.detach().numpy()[::4] - d["logits_1_every4"]).max() <= 1e-4 * np.abs(d["logits_1_every4"]).max()
     loss.backward()
+    # a gradient that is zero in exact arithmetic (the attention key bias: it shifts every logit of a query alike, and the softmax over
+    # the keys ignores that) is fp32 rounding noise in both runs, and its value depends on the host's CPU kernels: it must stay noise
+    noise = 1e-7 * float(d["grad_stats"][:, 0].max())
     errs = []
     for i, k in enumerate(names):
         g = sd["refmodel." + k].grad.reshape(-1).double()
         want = d["grad_stats"][i]
+        if want[0] <= noise:
+            assert g.norm().item() <= noise, (k, g.norm().item())
+            continue
         errs.append(max(abs(g.norm().item() - want[0]), abs((g * projection(k, g.numel())).sum().item() - want[2])) / want[0])
     assert max(errs) <= 2e-2 and np.median(errs) <= 1e-3, (max(errs), np.median(errs))
 
