@@ -14,7 +14,7 @@ _LIB_PATH = os.environ.get("GPEMSR_LIB_PATH") or os.path.join(os.path.dirname(os
 _lib = None
 
 MAX_SRC = 4
-ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_LRELU_SIGMOID = 0, 1, 2, 3, 4
+ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_LRELU_SIGMOID, ACT_ELU = 0, 1, 2, 3, 4, 5
 
 # every symbol include/gpemsr_hip.h declares (checked by tests/test_host_cpu.py::test_c_abi_library_exports_every_declared_symbol)
 SYMBOLS = [
@@ -43,6 +43,9 @@ SYMBOLS = [
     "gpemsr_copy_channels_f32_bf16", "gpemsr_conv2d_stem1_bf16", "gpemsr_conv2d_direct_bf16", "gpemsr_vgg_mask_bf16",
     "gpemsr_conv_c64_cout1_bf16", "gpemsr_upconv_out_c64_bf16", "gpemsr_conv7_c16_cout2_bf16", "gpemsr_conv_c64_cout1_f32", "gpemsr_upconv_out_c64_f32", "gpemsr_vq_codebook_loss", "gpemsr_conv7_c16_cout2_f32", "gpemsr_split_f32_bf16x2", "gpemsr_conv2d_gn_parts", "gpemsr_patch_cosine_finish",
     "gpemsr_conv2d_kernel_name", "gpemsr_conv2d_bf16_kernel_name", "gpemsr_conv7_c32_cout16_bf16", "gpemsr_conv7_c8_cout32_bf16", "gpemsr_conv2d_bf16_rowmax_parts", "gpemsr_rowmax_finish",
+    # affinity U-Net + sliding-window volume inference (csrc/conv3d.hip)
+    "gpemsr_conv3d", "gpemsr_conv3d_weight_floats", "gpemsr_upsample2_add_bn_elu", "gpemsr_affinity_gather", "gpemsr_affinity_accumulate",
+    "gpemsr_affinity_finalize",
 ]
 
 
@@ -81,6 +84,19 @@ class ConvDesc16(C.Structure):
         ("out32", C.c_void_p), ("out32_ld", C.c_int32),
         ("gn_partials", C.c_void_p), ("variant", C.c_int32), ("gn_cpg", C.c_int32),
         ("a_scale", C.c_void_p), ("a_shift", C.c_void_p), ("a_relu", C.c_int32), ("weight_forms", C.c_int32), ("rowmax", C.c_void_p),
+    ]
+
+
+class Conv3dDesc(C.Structure):
+    """gpemsr_conv3d_desc (include/gpemsr_hip.h), field by field."""
+    _fields_ = [
+        ("n", C.c_int32), ("d", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("inp", C.c_void_p), ("in_ld", C.c_int32), ("in_image_stride", C.c_int64),
+        ("cin", C.c_int32), ("cout", C.c_int32), ("kd", C.c_int32), ("ks", C.c_int32),
+        ("weight", C.c_void_p), ("bias", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p),
+        ("residual", C.c_void_p), ("res_ld", C.c_int32), ("res_image_stride", C.c_int64),
+        ("out", C.c_void_p), ("out_ld", C.c_int32), ("out_cstride", C.c_int64), ("out_image_stride", C.c_int64),
+        ("act", C.c_int32),
     ]
 
 
@@ -226,6 +242,12 @@ def load():
     lib.gpemsr_conv_c64_cout1_f32.argtypes = [p, i32, i32, i32, i32, p, p, i32, p, i32, p, i32, p, p]
     lib.gpemsr_upconv_out_c64_f32.argtypes = [p, i32, i32, i32, i32, p, p, p, i32, p]
     lib.gpemsr_vq_codebook_loss.argtypes = [p, i32, p, p, i64, i32, f32, f32, p, i32, p, p, i32, p, i64, p, p]
+    lib.gpemsr_conv3d.argtypes = [C.POINTER(Conv3dDesc), p]
+    lib.gpemsr_conv3d_weight_floats.argtypes = [i32, i32, i32, i32]
+    lib.gpemsr_upsample2_add_bn_elu.argtypes = [p, i32, p, i32, i32, i32, i32, i32, p, p, p, i32, p]
+    lib.gpemsr_affinity_gather.argtypes = [p, i32, i32, i32, i32, i32, i32, i32, p, i32, i32, i32, i32, p, p]
+    lib.gpemsr_affinity_accumulate.argtypes = [p, i32, p, p, i32, i32, i32, i32, p, p, i32, i32, i32, C.POINTER(C.c_int32), p]
+    lib.gpemsr_affinity_finalize.argtypes = [p, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, p, p]
     _lib = lib
     return lib
 

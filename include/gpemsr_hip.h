@@ -38,7 +38,8 @@ enum {
   GPEMSR_ACT_RELU = 1,          /* basicsr ResidualBlockNoBN, VGG, SpyNet, VQGAN blocks */
   GPEMSR_ACT_LRELU = 2,         /* LeakyReLU(0.1): model/GPEMSR.py:96,168,321 */
   GPEMSR_ACT_SIGMOID = 3,
-  GPEMSR_ACT_LRELU_SIGMOID = 4  /* sigmoid(lrelu(x)): model/GPEMSR.py:398-399 */
+  GPEMSR_ACT_LRELU_SIGMOID = 4, /* sigmoid(lrelu(x)): model/GPEMSR.py:398-399 */
+  GPEMSR_ACT_ELU = 5            /* x > 0 ? x : expm1(x): the affinity U-Net (gpemsr_conv3d only) */
 };
 
 int gpemsr_abi_version(void);
@@ -598,6 +599,47 @@ int gpemsr_png_encode_gray8_huff(const uint8_t* img, int n, int h, int w, int64_
  * header, 2 bad block, 3 bad Huffman table, 4 bad symbol / distance, 5 size mismatch, 6 input exhausted, 7 Adler-32 mismatch, 8 bad filter, 9 wider than 16,384 pixels (two scanlines live in LDS). */
 int gpemsr_png_decode_gray8(const uint8_t* idat, const int64_t* offsets, int n, int h, int w, uint8_t* raw, float* out, float divisor,
                             int32_t* status, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Affinity U-Net of the segmentation step (superhuman UNet_PNI, inference only) and its sliding-window volume inference; csrc/conv3d.hip.
+ * ------------------------------------------------------------------------- */
+/* 3-D convolution, stride 1, zero padding (kd/2, ks/2, ks/2), NDHWC float32 activations with a per-voxel stride:
+ *   out = act((conv(in, W) + bias + residual) * scale + shift), each term optional (NULL), scale / shift per channel (a folded BatchNorm).
+ * Kernels built: kd x ks x ks = 3x3x3, 1x3x3, 1x5x5, 1x1x1; cout <= 80; any cin.  weight: gpemsr_conv3d_weight_floats() floats in the
+ * packed layout [tap][cin/4][cout/16][k 4][n 16] (cin padded to 4, cout to 16 with zeros; tap = (kz*ks + ky)*ks + kx).
+ * Addresses: in + i*in_image_stride + voxel*in_ld + c; residual likewise with res_ld; out + i*out_image_stride + voxel*out_ld + c*out_cstride
+ * (NDHWC: out_cstride 1; NCDHW: out_ld 1, out_cstride d*h*w).  An image stride of 0 means dense (d*h*w*ld).  act: NONE, ELU or SIGMOID. */
+typedef struct {
+  int32_t n, d, h, w;
+  const float* in; int32_t in_ld; int64_t in_image_stride;
+  int32_t cin, cout, kd, ks;
+  const float* weight;
+  const float* bias;
+  const float* scale; const float* shift;
+  const float* residual; int32_t res_ld; int64_t res_image_stride;
+  float* out; int32_t out_ld; int64_t out_cstride; int64_t out_image_stride;
+  int32_t act;
+} gpemsr_conv3d_desc;
+int gpemsr_conv3d(const gpemsr_conv3d_desc* d, void* stream);
+/* floats of the packed weight of one gpemsr_conv3d layer (-1: cout outside 1..80) */
+int gpemsr_conv3d_weight_floats(int cin, int cout, int kd, int ks);
+/* The decoder's up_k + cat_k with the 1x1 convolution applied at the low resolution first: low [nimg][h][w][c] (ld lo_ld) ->
+ * out[nimg][2h][2w][c] = ELU((bilinear 2x, align_corners=True)(low) + skip) * scale + shift), skip / out at the high resolution. */
+int gpemsr_upsample2_add_bn_elu(const float* low, int lo_ld, const float* skip, int sk_ld, int nimg, int h, int w, int c,
+                                const float* scale, const float* shift, float* out, int out_ld, void* stream);
+/* Window gather of Provider_valid.__getitem__: vol [Z][H][W] (uint8 when is_u8, else float32), numpy 'reflect' padding (pz, py, px) applied on
+ * the fly (each pad < its extent), origins [nw][3] int32 (device) in padded coordinates -> out [nw][cz][cy][cx] float32; uint8 voxels are
+ * divided by 255 (IEEE division, as astype(float32) / 255.0). */
+int gpemsr_affinity_gather(const void* vol, int is_u8, int Z, int H, int W, int pz, int py, int px, const int32_t* origins, int nw,
+                           int cz, int cy, int cx, float* out, void* stream);
+/* Provider_valid.add_vol for windows affs [nw][nc][cz][cy][cx] at origins [nw][3] (device), in index order: out[c] += affs * wvol and
+ * wmap += wvol over the padded volume out [nc][Zp][Hp][Wp], wmap [Zp][Hp][Wp], bit-equal to numpy's float32 sequence (no FMA, no atomics).
+ * bbox (HOST array of 6: z, y, x, dz, dy, dx) bounds the voxels the windows touch. */
+int gpemsr_affinity_accumulate(const float* affs, int nc, const float* wvol, const int32_t* origins, int nw, int cz, int cy, int cx,
+                               float* out, float* wmap, int Zp, int Hp, int Wp, const int32_t* bbox, void* stream);
+/* Provider_valid.get_results: res [nc][Z][H][W] = (out / wmap)[:, pz:pz+Z, py:py+H, px:px+W] */
+int gpemsr_affinity_finalize(const float* out, const float* wmap, int nc, int Zp, int Hp, int Wp, int pz, int py, int px, int Z, int H,
+                             int W, float* res, void* stream);
 
 #ifdef __cplusplus
 }
