@@ -14,7 +14,7 @@ _LIB_PATH = os.environ.get("GPEMSR_LIB_PATH") or os.path.join(os.path.dirname(os
 _lib = None
 
 MAX_SRC = 4
-ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_LRELU_SIGMOID, ACT_ELU = 0, 1, 2, 3, 4, 5
+ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_LRELU_SIGMOID, ACT_ELU, ACT_LRELU_005 = 0, 1, 2, 3, 4, 5, 6
 
 # every symbol include/gpemsr_hip.h declares (checked by tests/test_host_cpu.py::test_c_abi_library_exports_every_declared_symbol)
 SYMBOLS = [
@@ -46,6 +46,9 @@ SYMBOLS = [
     # affinity U-Net + sliding-window volume inference (csrc/conv3d.hip)
     "gpemsr_conv3d", "gpemsr_conv3d_weight_floats", "gpemsr_upsample2_add_bn_elu", "gpemsr_affinity_gather", "gpemsr_affinity_accumulate",
     "gpemsr_affinity_finalize",
+    # MALA U-Net + last-wins window placement (csrc/conv3d_mala.hip)
+    "gpemsr_conv3d_valid_thin", "gpemsr_conv3d_valid_wide", "gpemsr_conv3d_valid_thin_weight_floats", "gpemsr_conv3d_valid_wide_weight_floats",
+    "gpemsr_conv3d_valid_wide_workspace_floats", "gpemsr_mala_merge", "gpemsr_maxpool133", "gpemsr_affinity_place",
 ]
 
 
@@ -96,6 +99,19 @@ class Conv3dDesc(C.Structure):
         ("weight", C.c_void_p), ("bias", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p),
         ("residual", C.c_void_p), ("res_ld", C.c_int32), ("res_image_stride", C.c_int64),
         ("out", C.c_void_p), ("out_ld", C.c_int32), ("out_cstride", C.c_int64), ("out_image_stride", C.c_int64),
+        ("act", C.c_int32),
+    ]
+
+
+class Conv3dValidDesc(C.Structure):
+    """gpemsr_conv3d_valid_desc (include/gpemsr_hip.h), field by field."""
+    _fields_ = [
+        ("n", C.c_int32), ("d", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("inp", C.c_void_p), ("in_ld", C.c_int32), ("in_image_stride", C.c_int64),
+        ("cin", C.c_int32), ("cout", C.c_int32),
+        ("weight", C.c_void_p), ("bias", C.c_void_p),
+        ("out", C.c_void_p), ("out_ld", C.c_int32), ("out_image_stride", C.c_int64),
+        ("workspace", C.c_void_p), ("workspace_floats", C.c_int64),
         ("act", C.c_int32),
     ]
 
@@ -248,6 +264,15 @@ def load():
     lib.gpemsr_affinity_gather.argtypes = [p, i32, i32, i32, i32, i32, i32, i32, p, i32, i32, i32, i32, p, p]
     lib.gpemsr_affinity_accumulate.argtypes = [p, i32, p, p, i32, i32, i32, i32, p, p, i32, i32, i32, C.POINTER(C.c_int32), p]
     lib.gpemsr_affinity_finalize.argtypes = [p, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, p, p]
+    lib.gpemsr_conv3d_valid_thin.argtypes = [C.POINTER(Conv3dValidDesc), p]
+    lib.gpemsr_conv3d_valid_wide.argtypes = [C.POINTER(Conv3dValidDesc), p]
+    for f in (lib.gpemsr_conv3d_valid_thin_weight_floats, lib.gpemsr_conv3d_valid_wide_weight_floats):
+        f.argtypes, f.restype = [i32, i32], C.c_int64
+    lib.gpemsr_conv3d_valid_wide_workspace_floats.argtypes = [i32] * 6
+    lib.gpemsr_conv3d_valid_wide_workspace_floats.restype = C.c_int64
+    lib.gpemsr_mala_merge.argtypes = [p, i32, i32, i32, i32, i32, i32, p, p, p, i32, p, i32, i32, i32, i32, p, i32, p]
+    lib.gpemsr_maxpool133.argtypes = [p, i32, i32, i32, i32, i32, p, i32, p]
+    lib.gpemsr_affinity_place.argtypes = [p, i32, p, i32, i32, i32, i32, p, i32, i32, i32, C.POINTER(C.c_int32), p]
     _lib = lib
     return lib
 

@@ -39,7 +39,8 @@ enum {
   GPEMSR_ACT_LRELU = 2,         /* LeakyReLU(0.1): model/GPEMSR.py:96,168,321 */
   GPEMSR_ACT_SIGMOID = 3,
   GPEMSR_ACT_LRELU_SIGMOID = 4, /* sigmoid(lrelu(x)): model/GPEMSR.py:398-399 */
-  GPEMSR_ACT_ELU = 5            /* x > 0 ? x : expm1(x): the affinity U-Net (gpemsr_conv3d only) */
+  GPEMSR_ACT_ELU = 5,           /* x > 0 ? x : expm1(x): the affinity U-Net (gpemsr_conv3d only) */
+  GPEMSR_ACT_LRELU_005 = 6      /* x > 0 ? x : 0.005 x: F.leaky_relu(x, 0.005) of the MALA U-Net (csrc/conv3d_mala.hip only) */
 };
 
 int gpemsr_abi_version(void);
@@ -640,6 +641,46 @@ int gpemsr_affinity_accumulate(const float* affs, int nc, const float* wvol, con
 /* Provider_valid.get_results: res [nc][Z][H][W] = (out / wmap)[:, pz:pz+Z, py:py+H, px:px+W] */
 int gpemsr_affinity_finalize(const float* out, const float* wmap, int nc, int Zp, int Hp, int Wp, int pz, int py, int px, int Z, int H,
                              int W, float* res, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * MALA 3-D U-Net of the segmentation step (UNet3D_MALA, inference only) and its last-wins window placement; csrc/conv3d_mala.hip.
+ * ------------------------------------------------------------------------- */
+/* Valid 3x3x3 convolution, stride 1, no padding: in [n][d][h][w] voxels -> out [n][d-2][h-2][w-2], NDHWC float32 with per-voxel strides
+ * in_ld / out_ld (image strides 0 = dense).  out = act(conv(in, W) + bias); act: NONE, LRELU_005 or SIGMOID; bias may be NULL.
+ * thin: cout <= 80, weight in the gpemsr_conv3d layout [27][cin/4][cout/16][k 4][n 16] (gpemsr_conv3d_valid_thin_weight_floats()).
+ * wide: any cout, weight [27][cin][coutp] with coutp = cout rounded up to 16 (zero columns), 16-byte aligned
+ * (gpemsr_conv3d_valid_wide_weight_floats()); K may be split over workgroups, which then needs workspace_floats >=
+ * gpemsr_conv3d_valid_wide_workspace_floats() (0: none needed).  tap = (kz*3 + ky)*3 + kx. */
+typedef struct {
+  int32_t n, d, h, w;
+  const float* in; int32_t in_ld; int64_t in_image_stride;
+  int32_t cin, cout;
+  const float* weight;
+  const float* bias;
+  float* out; int32_t out_ld; int64_t out_image_stride;
+  float* workspace; int64_t workspace_floats;
+  int32_t act;
+} gpemsr_conv3d_valid_desc;
+int gpemsr_conv3d_valid_thin(const gpemsr_conv3d_valid_desc* d, void* stream);
+int gpemsr_conv3d_valid_wide(const gpemsr_conv3d_valid_desc* d, void* stream);
+int64_t gpemsr_conv3d_valid_thin_weight_floats(int cin, int cout);
+int64_t gpemsr_conv3d_valid_wide_weight_floats(int cin, int cout);
+int64_t gpemsr_conv3d_valid_wide_workspace_floats(int n, int d, int h, int w, int cin, int cout);
+/* The MALA decoder merge mc = conv1x1(dconv(x)) + bias + crop(skip) in one pass: x [n][d][h][w][cin] (ld x_ld, dense images), dconv the
+ * depthwise ConvTranspose3d((1,3,3), stride (1,3,3), no bias) with dw [cin][9] (= weight[c][0][0][i][j]), the 1x1 weight [cin][coutp]
+ * (coutp = cout rounded up to 16, 16-byte aligned), bias [cout] or NULL, skip [n][sk_d][sk_h][sk_w][cout] (ld sk_ld) cropped by
+ * cz = (sk_d - d)/2 and c = (sk_h - 3h)/2 on BOTH H and W (crop_and_concat): out [n][d][3h][3w][cout] (ld out_ld) =
+ * (sum_c (x[c] * dw[c][3i+j]) * W[c][n] + bias[n]) + skip.  Shapes the reference cannot add (cz or c not positive, or a W difference other
+ * than 2c) are rejected. */
+int gpemsr_mala_merge(const float* x, int x_ld, int n, int d, int h, int w, int cin, const float* dw, const float* weight, const float* bias,
+                      int cout, const float* skip, int sk_ld, int sk_d, int sk_h, int sk_w, float* out, int out_ld, void* stream);
+/* MaxPool3d((1,3,3), stride (1,3,3)), floor: in [nimg][h][w][c] (ld in_ld) -> out [nimg][h/3][w/3][c] (ld out_ld) */
+int gpemsr_maxpool133(const float* in, int in_ld, int nimg, int h, int w, int c, float* out, int out_ld, void* stream);
+/* Provider_valid.add_vol for 'mala': window predictions preds [nw][nc][cz][cy][cx] at origins [nw][3] (device, output coordinates) are
+ * written into out [nc][Z][H][W]; where windows overlap the last one in index order wins (one thread per voxel, no atomics).  bbox (HOST
+ * array of 6: z, y, x, dz, dy, dx) bounds the voxels the windows touch. */
+int gpemsr_affinity_place(const float* preds, int nc, const int32_t* origins, int nw, int cz, int cy, int cx, float* out, int Z, int H, int W,
+                          const int32_t* bbox, void* stream);
 
 #ifdef __cplusplus
 }
